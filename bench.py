@@ -18,6 +18,9 @@ region; the timed region covers query + gather + MLPs + composite + all_gather f
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
+`--dump-outputs DIR` also writes what the last timed step computed (images, per-ray outputs, counters) as DIR/<name>.npy,
+so that two builds can be compared output for output: the inputs are seeded, the same arguments give the same arrays.
+
 Prints ONE JSON line (rank 0).  `value` is measured in the reference's arithmetic: --precision fp32 (default; every
 product and sum in fp32 on v_mfma_f32_32x32x2_f32), `roofline` prices the dominant kernel (the MLP chain
 k_shade_pairs) against the dense fp32 MFMA peak of 157.3 TFLOP/s.  `other_mode` holds the same workload, same
@@ -221,6 +224,36 @@ def pmc_traffic_sum(kernels, workload_key):
             except (OSError, KeyError, ValueError):
                 continue
     return None
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Writes every array of `arrays` (name -> CPU tensor) as out_dir/<name>.npy, float32 (float64 for int64 data, which
+    float32 would round).  When all of them together exceed `budget` bytes, each is cut to a fixed, seeded sample of
+    its rows (flattened over every dimension but the last for multi-channel arrays) that keeps the total under the
+    budget, and the row numbers taken go beside it as <name>_rows.npy (float64); arrays of at most 1024 rows stay whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: a.to(torch.float64 if a.dtype == torch.int64 else torch.float32) for n, a in arrays.items()}
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    sampled = total > budget
+    if sampled:
+        rows = {n: a.reshape(-1, a.shape[-1]) if a.dim() > 1 and a.shape[-1] <= 4 else a.reshape(-1, 1)
+                for n, a in arrays.items() if a.numel() > 1024}
+        small = total - sum(r.numel() * r.element_size() for r in rows.values())
+        # + 8 bytes per row taken: its float64 row number; 64 kB for the .npy headers
+        total_rows = sum(r.shape[0] * (r.shape[1] * r.element_size() + 8) for r in rows.values())
+        gen = torch.Generator().manual_seed(seed)
+        for n, r in rows.items():
+            k = r.shape[0] * (budget - small - 65536) // total_rows
+            keep = torch.randperm(r.shape[0], generator=gen)[:k].sort().values
+            arrays[n] = r.index_select(0, keep).squeeze(-1)
+            np.save(os.path.join(out_dir, f"{n}_rows.npy"), keep.to(torch.float64).numpy())
+    for n, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{n}.npy"), a.contiguous().numpy())
+    return {"dir": out_dir, "arrays": sorted(arrays), "sampled": sampled, "full_bytes": total}
 
 
 def cfg0_leg(args, dev):
@@ -435,6 +468,12 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3"],
                     help="MLP arithmetic of `value`: fp32 MFMA (the reference's arithmetic), or the opt-in 3 bf16 MFMAs "
                          "per fp32 product (hi/lo split)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; at most 64 MB, a fixed "
+                         "seeded sample of rows beyond that): image_rgb / image_depth, the step's assembled [views, H, "
+                         "W] images (not under --emulate-world, where only this rank's tiles exist); rays_rgb / "
+                         "rays_depth / rays_acc / rays_mask, the render call's per-ray outputs for this rank's rays "
+                         "(view-major, shard order); counters, its device counters")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -685,6 +724,16 @@ def main():
 
     run_steps(rnd, 0, args.warmup)
     elapsed, acc_ms, acc_cnt, n_launch = timed(rnd, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs and (rank == 0 or emulate):
+        # the last timed step's results, before any later leg reuses `outs` and the pipe
+        arrays = {}
+        if not emulate:
+            img = pipe.images.reshape(world, H, W, 4).cpu()
+            arrays.update(image_rgb=img[..., :3], image_depth=img[..., 3])
+        arrays.update(rays_rgb=outs["rgb"].cpu(), rays_depth=outs["depth"].cpu(), rays_acc=outs["acc"].cpu(),
+                      rays_mask=outs["ray_mask"].cpu(), counters=outs["counters_dev"].cpu())
+        dumped = dump_outputs(args.dump_outputs, arrays)
     rays_per_step = world * H * W
     value = rays_per_step * args.steps / elapsed
 
@@ -844,6 +893,8 @@ def main():
         }
         if rccl_world is not None:
             result["rccl_world"] = rccl_world
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if alt is not None:
             result["other_mode"] = alt
         if early is not None:

@@ -7,21 +7,24 @@ The shipped files are MVSNet-initialisation checkpoints: they carry `aggregator.
 `neural_points.*` tensors -- those appear in the per-scene `{iter}_net_ray_marching.pth` that training writes
 (models/base_model.py:85-120), whose layout tests/test_gpu_checkpoint.py reproduces.
 
-  python oracle/gen_checkpoint_listing.py
+  python oracle/gen_checkpoint_listing.py <reference checkout>
 """
+import argparse
 import glob
 import json
 import os
 
 import torch
 
-REF = "/root/reference/pointnerf/mvsnet_checkpoints/init"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "shipped_checkpoint_keys.json")
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("reference", help="checkout of the reference (the directory that holds pointnerf/)")
+    init = os.path.join(ap.parse_args().reference, "pointnerf", "mvsnet_checkpoints", "init")
     listing = {}
-    for path in sorted(glob.glob(os.path.join(REF, "*", "best_net_ray_marching.pth"))):
+    for path in sorted(glob.glob(os.path.join(init, "*", "best_net_ray_marching.pth"))):
         sd = torch.load(path, map_location="cpu", weights_only=True)
         name = os.path.basename(os.path.dirname(path))
         listing[name] = {k: {"shape": list(v.shape), "dtype": str(v.dtype).replace("torch.", "")} for k, v in sd.items()}

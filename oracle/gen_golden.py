@@ -1,10 +1,10 @@
 """Generates tests/golden/*.npz by RUNNING the reference's own CPU-importable code.
 
-Runs only in the build container (needs /root/reference); the GPU box receives the
-committed fixtures, never reference source.  Fixtures are data: seeded inputs and the
+Runs only where a checkout of the reference is at hand (its path is the one argument); the GPU
+box receives the committed fixtures, never reference source.  Fixtures are data: seeded inputs and the
 reference's outputs.  Recipe: SURVEY.md Appendix B.
 
-  python oracle/gen_golden.py            # rewrites tests/golden/ref_*.npz
+  python oracle/gen_golden.py <reference checkout>     # rewrites tests/golden/ref_*.npz
 
 What is pinned:
   ref_raygen.npz      near_far_linear_ray_generation   (diff_ray_marching.py:292-336), jitter 0
@@ -31,7 +31,7 @@ import types
 import numpy as np
 import torch
 
-REF = "/root/reference/pointnerf"
+REF = None   # <reference checkout>/pointnerf, set by main()
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
 
 
@@ -129,14 +129,14 @@ def run_aggregator(agg, inp, widen=True, conf=None, full=False):
     return decoded, valid
 
 
-SHIPPED = f"{REF}/mvsnet_checkpoints/init/dtu_dgt_d012_img0123_conf_agg2_32_dirclr20/best_net_ray_marching.pth"
+SHIPPED = "mvsnet_checkpoints/init/dtu_dgt_d012_img0123_conf_agg2_32_dirclr20/best_net_ray_marching.pth"
 
 
 def trained_fixture():
     """The shipped trained aggregator through the reference's forward on seeded inputs,
     at the slope it was trained with (0.01) and at the plugin's (0.1).  The tensors are stored under the plugin's
     module names (NAME_MAP) so the oracle and the HIP path load them as they load any weights."""
-    sd = torch.load(SHIPPED, map_location="cpu", weights_only=True)
+    sd = torch.load(os.path.join(REF, SHIPPED), map_location="cpu", weights_only=True)
     agg_sd = {k[len("aggregator."):]: v.float() for k, v in sd.items() if k.startswith("aggregator.")}
     save = {}
     for slope, tag in ((0.01, "s001"), (0.1, "s01")):
@@ -166,6 +166,10 @@ def to_np(d):
 
 
 def main():
+    global REF
+    ap = argparse.ArgumentParser(description="tests/golden/ref_*.npz from the reference's own code")
+    ap.add_argument("reference", help="checkout of the reference (the directory that holds pointnerf/)")
+    REF = os.path.join(os.path.abspath(ap.parse_args().reference), "pointnerf")
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
     drm = load_drm()

@@ -1,6 +1,6 @@
 """Host-side pieces of bench.py that need no GPU: the core / thread accounting of the CPU-baseline legs, and the lookup of
 the committed PMC passes that `roofline.traffic` / `roofline_hbm.traffic` quote (only for the very workload they were
-collected on)."""
+collected on), and the writer of --dump-outputs."""
 import importlib.util
 import json
 import os
@@ -50,3 +50,34 @@ def test_pmc_lookup_matches_the_workload_key_only():
     assert abs(sum(q[1].values()) - q[0]) < 1.0
     with open(os.path.join(ROOT, q[2])) as f:
         assert json.load(f)["workload_key"] == key
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_under_the_budget(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files; over the budget every large array is cut to the same seeded rows
+    on every run (their numbers beside it), small ones stay whole, and the files stay under the budget."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(1)
+    arrays = {"image_rgb": torch.rand(2, 200, 200, 4, generator=g)[..., :3],
+              "image_depth": torch.rand(2, 200, 200, generator=g),
+              "rays_mask": torch.randint(0, 2, (80000,), generator=g).to(torch.int8),
+              "counters": torch.arange(10, dtype=torch.int64)}
+    whole = b.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert not whole["sampled"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "image_rgb.npy"), arrays["image_rgb"].numpy())
+    assert np.load(tmp_path / "whole" / "rays_mask.npy").dtype == np.float32
+    assert np.load(tmp_path / "whole" / "counters.npy").dtype == np.float64
+    budget = 600_000
+    for d in ("a", "b"):
+        assert b.dump_outputs(str(tmp_path / d), arrays, budget=budget)["sampled"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    for f in files:
+        x = np.load(tmp_path / "a" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, np.load(tmp_path / "b" / f)), f
+    rows = np.load(tmp_path / "a" / "image_rgb_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 80000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "image_rgb.npy"), arrays["image_rgb"].reshape(-1, 3).numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "counters.npy"), np.arange(10.0))
